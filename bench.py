@@ -18,6 +18,7 @@ per GPU) before this process touches the GPU, relays rank 0's line and adds the 
 (gprf_create_multi: one process, N devices) from a second child; under torch.distributed.run it is one of the ranks.
 `value` = steps / the MEDIAN wall time of REPS repetitions of the timed loop (every repetition: exactly --steps
 evaluations between barrier + synchronize; all samples in "ms_per_step_samples").
+`--dump-outputs DIR` writes what the last timed step returned (ll, grad_X, and grad_cov for task xcov) as DIR/<name>.npy.
 
 Rank 0 prints ONE JSON line.  Extra keys: "roofline" (dominant kernel, HIP-event timed inside the timed region),
 "cpu_baseline" (the oracle's CPU port on this box's host cores), "stages_ms", "device_resident_evals_per_s" (the
@@ -101,7 +102,39 @@ def parse():
     ap.add_argument("--reps", type=int, default=REPS, help="repetitions of the timed loop (value = median)")
     ap.add_argument("--no-single-process-leg", action="store_true",
                     help="self-launched N > 1 run: skip the second child (one process driving the N devices)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (ll, grad_X[, grad_cov]) as "
+                         "DIR/<name>.npy (float64); the same arguments give the same inputs, so two builds compare output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)      # (the ranks of a self-launched run start in ROOT)
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs writes at most this much; a larger gradient is sampled by rows
+
+
+def dump_outputs(out_dir, out):
+    """The timed path's last result (ll, gradX, gradCov as GPRF.llgrad returns them) -> out_dir/<name>.npy, float64.
+    Should the arrays exceed DUMP_LIMIT_BYTES, a fixed seeded sample of gradient rows is written instead, with its row
+    indices (grad_X_rows.npy).  -> {name: shape} of what was written"""
+    ll, gX, gC = out
+    arrays = {"ll": np.array([ll], dtype=np.float64), "grad_X": np.asarray(gX, dtype=np.float64)}
+    if np.size(gC):
+        arrays["grad_cov"] = np.asarray(gC, dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n, row_bytes = arrays["grad_X"].shape[0], arrays["grad_X"][0].nbytes + 8       # (+ its index)
+        keep = min(n, (DUMP_LIMIT_BYTES - (total - arrays["grad_X"].nbytes)) // row_bytes)
+        rows = np.sort(np.random.RandomState(0).choice(n, size=keep, replace=False))
+        arrays["grad_X"] = arrays["grad_X"][rows]
+        arrays["grad_X_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def algorithmic_flops(sizes, dy):
@@ -309,6 +342,12 @@ def launch_ranks(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     me = os.path.abspath(__file__)
     argv = [a for a in sys.argv[1:] if a != "--no-single-process-leg"]
+    if args.dump_outputs is not None:       # (the children start in ROOT: hand them the directory as an absolute path)
+        argv = [a for a in argv if not a.startswith("--dump-outputs=")]
+        if "--dump-outputs" in argv:
+            i = argv.index("--dump-outputs")
+            del argv[i:i + 2]
+        argv += ["--dump-outputs", args.dump_outputs]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), me] + argv
     t0 = time.perf_counter()
@@ -333,7 +372,9 @@ def launch_ranks(args):
     if not args.no_single_process_leg:
         sp = {"value": None}
         try:
-            cmd2 = [sys.executable, me, "--single-process", "--only-north-star", "--no-cpu-baseline"] + argv
+            # (a side figure: the dump, if asked for, is the ranks' last step and stays theirs)
+            argv2 = argv[:-2] if args.dump_outputs is not None else argv
+            cmd2 = [sys.executable, me, "--single-process", "--only-north-star", "--no-cpu-baseline"] + argv2
             r2 = subprocess.run(cmd2, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200)
             l2 = _last_json_line(r2.stdout or "")
             if r2.returncode == 0 and l2 is not None:
@@ -421,10 +462,11 @@ def main():
         sd.set_centers(grid_centers(nblocks))
         return sd
 
-    def sequential_rate(g, Xlist, steps, warmup, grad_cov, reps=1):
+    def sequential_rate(g, Xlist, steps, warmup, grad_cov, reps=1, last=None):
         """THE metric's loop: update_X + llgrad, one evaluation finished before the next starts, nothing else in the
         timed region (no events).  `reps` repetitions, each EXACTLY `steps` evaluations between barrier + synchronize
-        (max over ranks); -> (evals/s at the median repetition, its ms per step, ms per step of every repetition)"""
+        (max over ranks); -> (evals/s at the median repetition, its ms per step, ms per step of every repetition).
+        `last` (a list) receives a copy of what the last timed step returned, taken outside the timed region"""
         nXl = len(Xlist)
         for k in range(warmup):
             g.update_X(Xlist[k % nXl])
@@ -435,9 +477,11 @@ def main():
             t0 = time.perf_counter()
             for k in range(steps):
                 g.update_X(Xlist[k % nXl])
-                g.llgrad(grad_X=True, grad_cov=grad_cov)
+                out = g.llgrad(grad_X=True, grad_cov=grad_cov)
             barrier()
             el = time.perf_counter() - t0
+            if last is not None:
+                last[:] = [float(out[0])] + [np.array(a, copy=True) for a in out[1:]]
             if world > 1:
                 tt = torch.tensor([el], dtype=torch.float64, device=dev)
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -489,7 +533,9 @@ def main():
     g = (sd.build_gprf(local_dist=args.local_dist, devices=devices) if devices is not None else
          sd.build_gprf(local_dist=args.local_dist, device=local_rank, shard=(rank, world)))
     n_members = len(devices) if devices is not None else world      # devices working on ONE evaluation
-    value, ms_per_step, ms_samples = sequential_rate(g, Xlist, args.steps, args.warmup, grad_cov, args.reps)
+    last_out = []
+    value, ms_per_step, ms_samples = sequential_rate(g, Xlist, args.steps, args.warmup, grad_cov, args.reps, last=last_out)
+    dumped = dump_outputs(args.dump_outputs, last_out) if (args.dump_outputs is not None and rank == 0) else None
     # who really took part: ranks of the collective's backend, devices this process sees, units per shard
     if devices is not None:
         nm, on_host, devs_used, shard_units = g._ctx.group_info()
@@ -512,7 +558,8 @@ def main():
         if rank == 0:
             print(json.dumps({"diagnostic": "headline only (no per-kernel timing pass)", "value": value,
                               "unit": "evals/s", "ms_per_step": ms_per_step, "n_gpus": n_members,
-                              "ms_per_step_samples": [round(v, 5) for v in ms_samples], "library": _capi.runtime_config()}))
+                              "ms_per_step_samples": [round(v, 5) for v in ms_samples], "library": _capi.runtime_config(),
+                              **({"dumped_outputs": dumped} if dumped is not None else {})}))
         g.close()
         if dist.is_initialized():
             dist.barrier()
@@ -628,6 +675,8 @@ def main():
                             "'launch_wide' is the same loop with that pipelining off" % (cnt, ms_with_events),
             "host_gap_ms": None,      # (meaningful only where the stages run one after the other: launch_wide.host_gap_ms)
         }
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
         # the same timed loop with the by-class pipelining off (GPRF_DIAG solve_class=0): what the stage times above add up to
         if n_members == 1:
             prev = os.environ.get("GPRF_DIAG")

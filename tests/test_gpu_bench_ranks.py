@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -76,14 +77,15 @@ def test_plain_python_bench_gpus_2_launches_the_ranks_itself():
     assert sp["group"]["members"] == 2
 
 
-def test_eight_ranks_dry_run_on_one_gpu():
-    """`python bench.py --gpus 8` as the scaling driver calls it, on a one-GPU box: eight ranks time-share GPU 0 over gloo
-    (GPRF_BENCH_ONE_GPU=1).  Nothing N = 2 never touched may stop the first real 8-GPU run: eight shards, every unit on
-    exactly one rank, one contract line, rc 0."""
+def test_four_ranks_dry_run_on_one_gpu():
+    """`python bench.py --gpus 4` as the scaling driver calls it, on a one-GPU box: four ranks time-share GPU 0 over gloo
+    (GPRF_BENCH_ONE_GPU=1).  Nothing N = 2 never touched may stop the first real multi-GPU run: four shards, every unit on
+    exactly one rank, one contract line, rc 0.  (Four, not eight: with this process, at most five processes have the
+    GPU open at once; eight shards are checked in one process by the test below.)"""
     env = dict(os.environ, GPRF_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "5", "--warmup", "2", "--reps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "5", "--warmup", "2", "--reps", "3",
            "--ntrain", "3000", "--nblocks", "36", "--yd", "8", "--no-c4", "--no-c5", "--no-cpu-baseline",
            "--no-single-process-leg"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
@@ -91,9 +93,48 @@ def test_eight_ranks_dry_run_on_one_gpu():
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 8 and d["steps"] == 5 and d["value"] > 0
+    assert d["n_gpus"] == 4 and d["steps"] == 5 and d["value"] > 0
     assert d["collective_backend"] == "gloo" and d["rccl_ranks"] == 0
+    assert len(d["shard_units"]) == 4 and sum(d["shard_units"]) == 36 + len_pairs(36) and min(d["shard_units"]) > 0
+
+
+def test_eight_shards_single_process_on_one_gpu():
+    """`bench.py --single-process --gpus 8` on a one-GPU box: eight members on GPU 0, driven by ONE process
+    (gprf_create_multi).  Eight shards, every unit on exactly one member, one contract line, rc 0."""
+    env = dict(os.environ, GPRF_BENCH_ONE_GPU="1")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--single-process", "--gpus", "8", "--steps", "5", "--warmup", "2",
+           "--reps", "3", "--ntrain", "3000", "--nblocks", "36", "--yd", "8", "--no-c4", "--no-c5", "--no-cpu-baseline"]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 8 and d["steps"] == 5 and d["value"] > 0 and "ONE process" in d["config"]["parallelism"]
+    assert d["config"]["group"]["members"] == 8
     assert len(d["shard_units"]) == 8 and sum(d["shard_units"]) == 36 + len_pairs(36) and min(d["shard_units"]) > 0
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's ll and gradient as float64 .npy files, named in the result line;
+    the same arguments twice give the same inputs, hence the same bytes."""
+    dumps = []
+    for i in range(2):
+        out = tmp_path / ("d%d" % i)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--reps", "2",
+               "--ntrain", "2000", "--nblocks", "16", "--yd", "8", "--only-north-star", "--no-cpu-baseline", "--no-parity",
+               "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 7 and d["ms_per_step"] > 0
+        assert d["dumped_outputs"] == {"ll": [1], "grad_X": [2000, 2]}
+        ll, gX = np.load(str(out / "ll.npy")), np.load(str(out / "grad_X.npy"))
+        assert ll.dtype == np.float64 and gX.dtype == np.float64 and np.all(np.isfinite(ll)) and np.all(np.isfinite(gX))
+        assert np.abs(gX).max() > 0
+        dumps.append((ll, gX))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
 
 
 def len_pairs(nblocks):

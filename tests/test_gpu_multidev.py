@@ -159,26 +159,37 @@ def test_host_staged_slots_give_the_same_bits(monkeypatch):
     peer.close(); host.close()
 
 
-def test_group_over_distinct_devices_when_the_box_has_them():
-    """The xGMI hop itself: members on DIFFERENT physical GPUs (skipped on one-GPU boxes — the hop has never run there)."""
+def test_group_over_distinct_devices_when_the_box_has_them(monkeypatch):
+    """The xGMI hop itself: members on DIFFERENT physical GPUs, twenty evaluations against the single-device result.  On a
+    one-GPU box the hop cannot run: there the same twenty evaluations run with both members on GPU 0, once with the
+    partial vectors meeting on the first device (peer stores) and once in pinned host memory (the form distinct GPUs
+    without peer access take) — everything of the group but the hop."""
     import torch
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs")
     from gprf_amd.gprf import GPRF
     X, Y, b, cov = _case()
     nbrs = b.neighbors()
-    one = GPRF(X, Y, b.block_clusters, cov, 0.01, neighbors=nbrs)
-    grp = GPRF(X, Y, b.block_clusters, cov, 0.01, neighbors=nbrs, devices=[0, 1])
-    rng = np.random.RandomState(2)
-    Xk = X
-    for _ in range(20):      # repeated evaluations: a stale slot from the evaluation before would show
-        Xk = Xk + 0.005 * rng.randn(*X.shape)
-        one.update_X(Xk); grp.update_X(Xk)
-        a, c = one.llgrad(grad_X=True, grad_cov=True), grp.llgrad(grad_X=True, grad_cov=True)
-        assert np.isclose(a[0], c[0], rtol=1e-12) and np.allclose(a[1], c[1], rtol=0, atol=1e-11 * np.abs(a[1]).max())
-        assert np.allclose(a[2], c[2], rtol=1e-10)
-    assert grp._ctx.group_info()[2] == [0, 1]
-    one.close(); grp.close()
+    if torch.cuda.device_count() >= 2:
+        forms = [([0, 1], None)]
+    else:
+        forms = [([0, 0], None), ([0, 0], "1")]
+    for devices, host_slots in forms:
+        one = GPRF(X, Y, b.block_clusters, cov, 0.01, neighbors=nbrs)
+        if host_slots is not None:
+            monkeypatch.setenv("GPRF_GROUP_HOST_SLOTS", host_slots)
+        grp = GPRF(X, Y, b.block_clusters, cov, 0.01, neighbors=nbrs, devices=devices)
+        monkeypatch.delenv("GPRF_GROUP_HOST_SLOTS", raising=False)
+        if host_slots is not None:
+            assert grp._ctx.group_info()[1] is True
+        rng = np.random.RandomState(2)
+        Xk = X
+        for _ in range(20):      # repeated evaluations: a stale slot from the evaluation before would show
+            Xk = Xk + 0.005 * rng.randn(*X.shape)
+            one.update_X(Xk); grp.update_X(Xk)
+            a, c = one.llgrad(grad_X=True, grad_cov=True), grp.llgrad(grad_X=True, grad_cov=True)
+            assert np.isclose(a[0], c[0], rtol=1e-12) and np.allclose(a[1], c[1], rtol=0, atol=1e-11 * np.abs(a[1]).max())
+            assert np.allclose(a[2], c[2], rtol=1e-10)
+        assert grp._ctx.group_info()[2] == devices
+        one.close(); grp.close()
 
 
 def test_create_failures_say_why():
