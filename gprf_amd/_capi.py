@@ -65,6 +65,11 @@ SIGNATURES = {
     "gprf_build_flags": (ctypes.c_char_p, []),
     "gprf_runtime_config": (ctypes.c_char_p, []),
     "gprf_group_info": (ctypes.c_int, [_vp, _i32p, _i32p, _i32, _i32p, _i32p]),
+    "gprf_predictor_create": (ctypes.c_int, [_vp, _dp, _dp, ctypes.POINTER(_vp), _i32p]),
+    "gprf_predictor_destroy": (ctypes.c_int, [_vp]),
+    "gprf_predictor_last_error": (ctypes.c_char_p, [_vp]),
+    "gprf_predict": (ctypes.c_int, [_vp, _i32, _dp, _i32, _i64p, _i32p, _i64p, _i32p, _dp, _i32, ctypes.c_double, _dp, _dp,
+                                    _i32p]),
     "gprf_debug_run": (ctypes.c_int, [_vp, _dp, _i32]),
     "gprf_debug_fetch": (ctypes.c_int, [_vp, _i32, _i32, _dp, ctypes.c_int64]),
     "gprf_debug_unit_shape": (ctypes.c_int, [_vp, _i32, _i32p, _i32p, _i32p]),
@@ -462,3 +467,77 @@ class Context(object):
         out = np.zeros(shape)
         self._check(self.lib.gprf_debug_fetch(self.h, l, what, dptr(out), out.size), "gprf_debug_fetch")
         return out
+
+
+PRED_MAX_T = 512
+
+
+class Predictor(object):
+    """Thin RAII wrapper over gprf_predictor* (gprf_predictor_create / gprf_predict, include/gprf_hip.h)."""
+
+    def __init__(self, ctx, X, Y=None):
+        self.lib = ctx.lib
+        self.h = _vp()
+        self.dx, self.dy = ctx.dx, ctx.dy
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        assert X.shape == (ctx.n, ctx.dx)
+        if Y is not None:
+            Y = np.ascontiguousarray(Y, dtype=np.float64)
+            if Y.shape != (ctx.n, ctx.dy):
+                raise ValueError("Y must be %d x %d, the shape of the training targets" % (ctx.n, ctx.dy))
+        bad = _i32(-1)
+        rc = self.lib.gprf_predictor_create(ctx.h, dptr(X), dptr(Y) if Y is not None else None, ctypes.byref(self.h),
+                                            ctypes.byref(bad))
+        if rc == GPRF_NOT_PD:
+            self.h = None
+            raise NotPositiveDefinite(self.lib.gprf_last_error(ctx.h).decode(), bad.value)
+        if rc != GPRF_OK:
+            self.h = None
+            raise GprfHipError("gprf_predictor_create failed (%d): %s" % (rc, self.lib.gprf_last_error(ctx.h).decode()))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gprf_predictor_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def predict(self, Xs, groups, sources, prior_theta, test_noise_var):
+        """groups: list of test row index arrays; sources: list of block id lists (one per group) ->
+        (list of t x dy means, list of t x t covariances), one per group."""
+        if self.h is None:
+            raise GprfHipError("the predictor has been closed")
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64).reshape(-1, self.dx)
+        gptr = np.zeros(len(groups) + 1, dtype=np.int64)
+        gptr[1:] = np.cumsum([len(g) for g in groups])
+        rows = np.concatenate([np.asarray(g, dtype=np.int32).ravel() for g in groups]) if gptr[-1] else np.zeros(0, np.int32)
+        sptr = np.zeros(len(groups) + 1, dtype=np.int64)
+        sptr[1:] = np.cumsum([len(s) for s in sources])
+        srcs = np.concatenate([np.asarray(list(s), dtype=np.int32).ravel() for s in sources]) if sptr[-1] else np.zeros(0, np.int32)
+        rows, srcs = rows.astype(np.int32), srcs.astype(np.int32)
+        th = np.ascontiguousarray(prior_theta, dtype=np.float64).ravel()
+        ts = [len(g) for g in groups]
+        mean = np.empty(max(sum(t * self.dy for t in ts), 1))
+        cov = np.empty(max(sum(t * t for t in ts), 1))
+        bad = _i32(-1)
+        rc = self.lib.gprf_predict(self.h, Xs.shape[0], dptr(Xs), len(groups), gptr.ctypes.data_as(_i64p),
+                                   rows.ctypes.data_as(_i32p), sptr.ctypes.data_as(_i64p), srcs.ctypes.data_as(_i32p),
+                                   dptr(th), th.size, float(test_noise_var), dptr(mean), dptr(cov), ctypes.byref(bad))
+        msg = self.lib.gprf_predictor_last_error(self.h).decode()
+        if rc == GPRF_NOT_PD:
+            raise NotPositiveDefinite(msg, bad.value)
+        if rc == -1:
+            raise ValueError(msg)
+        if rc != GPRF_OK:
+            raise GprfHipError("gprf_predict failed (%d): %s" % (rc, msg))
+        means, covs, om, oc = [], [], 0, 0
+        for t in ts:
+            means.append(mean[om:om + t * self.dy].reshape(t, self.dy).copy())
+            covs.append(cov[oc:oc + t * t].reshape(t, t).copy())
+            om += t * self.dy
+            oc += t * t
+        return means, covs

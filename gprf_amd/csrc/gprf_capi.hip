@@ -2249,3 +2249,271 @@ int gprf_debug_fetch(gprf_ctx *c, int32_t l, int32_t what, double *out, int64_t 
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ prediction
+// GPRF.train_predictor / predict (gprf.py:593-672): see include/gprf_hip.h and gprf_predict.hip.
+struct gprf_predictor {
+    int device = 0, dist_id = 0, kern_id = 0, dx = 0, dy = 0, n_blocks = 0, rs = XPAD, ndfn = 0;
+    hipStream_t stream = nullptr;
+    KParams kp{};
+    std::vector<int32_t> b_m, b_row;      // per block: points, first row in the alpha / record pools
+    std::vector<int64_t> b_mat;           // ... element offset of its W
+    DevBuf<double> W, A, X;               // the snapshot
+    DevBuf<char> tab;                     // per call: tasks | groups | items | test point records
+    PinBuf<char> h_tab;                   // ... staged here (k_pred_stage copies it up)
+    PinBuf<double> h_res;                 // per call: means | covariances, stored by k_pred_fuse
+    PinBuf<int32_t> h_status;             // per call: per group, stored by k_pred_fuse
+    DevBuf<double> Kt, V, C, Mn, ws;
+    std::string err;
+};
+
+namespace {
+
+int pfail(gprf_predictor *p, int code, const std::string &msg) {
+    if (p) p->err = msg;
+    return code;
+}
+
+#define PHIP_TRY(p, expr)                                                                          \
+    do {                                                                                           \
+        hipError_t e__ = (expr);                                                                   \
+        if (e__ != hipSuccess)                                                                     \
+            return pfail((p), GPRF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));   \
+    } while (0)
+
+size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+}  // namespace
+
+extern "C" {
+
+int gprf_predictor_create(gprf_ctx *c, const double *X, const double *Y, gprf_predictor **out, int32_t *bad_block) {
+    if (out) *out = nullptr;
+    if (bad_block) *bad_block = -1;
+    if (!c || !X || !out) return GPRF_ERR_ARG;
+    GROUP_REFUSE(c, "gprf_predictor_create")
+    if (c->world > 1) return fail(c, GPRF_ERR_STATE, "gprf_predictor_create is not available on a sharded context");
+    int rc = check_ready(c);
+    if (rc != GPRF_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->ev_last) HIP_TRY(c, hipEventSynchronize(c->ev_last));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t ny = (size_t)c->n * c->dy;
+    DevBuf<double> saved_Y;
+    if (Y) {      // train_predictor(Y=...): the alphas from these targets (gprf.py:595-596); the context's Y is put back below
+        HIP_TRY(c, saved_Y.reserve(ny, 1.0));
+        HIP_TRY(c, hipMemcpy(saved_Y.p, c->d_Y.p, ny * sizeof(double), hipMemcpyDeviceToDevice));
+        HIP_TRY(c, hipMemcpy(c->d_Y.p, Y, ny * sizeof(double), hipMemcpyHostToDevice));
+    }
+    size_t nx = (size_t)c->n * c->dx;
+    memcpy(c->h_X.p, X, nx * sizeof(double));
+    HIP_TRY(c, hipMemcpyAsync(c->d_X.p, c->h_X.p, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    rc = enqueue_eval(c, c->d_X.p, 0, 0, c->d_out.p, c->stream, 3, false);      // up to At: W = U^-T, At = (K^-1 Y)^T
+    hipError_t es = rc == GPRF_OK ? hipStreamSynchronize(c->stream) : hipSuccess;
+    c->eval_pending = false;
+    if (Y) {
+        (void)hipStreamSynchronize(c->stream);
+        HIP_TRY(c, hipMemcpy(c->d_Y.p, saved_Y.p, ny * sizeof(double), hipMemcpyDeviceToDevice));
+        saved_Y.release();
+    }
+    if (rc != GPRF_OK) return rc;
+    if (es != hipSuccess) return fail(c, GPRF_ERR_HIP, std::string("predictor build: ") + hipGetErrorString(es));
+    if (c->h_res.p[CTL_OVERFLOW]) return fail(c, GPRF_ERR_STATE, "predictor build: the partition outgrew the workspace; evaluate once first");
+    refresh_host_units(c);
+
+    gprf_predictor *p = new gprf_predictor();
+    p->device = c->device; p->dist_id = c->dist_id; p->kern_id = c->kern_id; p->dx = c->dx; p->dy = c->dy; p->ndfn = c->ndfn;
+    p->n_blocks = c->n_blocks; p->rs = c->dist_id == GPRF_DIST_LLD ? 8 : XPAD;
+    p->kp = make_kparams(c);
+    p->b_m.assign(c->n_blocks, 0); p->b_row.assign(c->n_blocks, 0); p->b_mat.assign(c->n_blocks, 0);
+    std::vector<PredGather> gl;
+    int64_t mat = 0, rows = 0;
+    int max_m = 0, first_bad = -1;
+    for (int l = 0; l < c->n_local; ++l) {
+        const int b = c->l_global[l];
+        if (b >= c->n_blocks) continue;      // (the pairs: not part of a predictor)
+        const int m = c->l_m[l], mp = pad16(m);
+        if (m > 0 && c->h_res.p[CTL_WORDS + l] != 0 && (first_bad < 0 || b < first_bad)) first_bad = b;
+        p->b_m[b] = m; p->b_row[b] = (int32_t)rows; p->b_mat[b] = mat;
+        if (m > 0) gl.push_back(PredGather{c->l_matoff[l], mat, c->l_rowoff[l], (int32_t)rows, m, 0});
+        mat += (int64_t)mp * mp;
+        rows += mp;
+        max_m = std::max(max_m, m);
+    }
+    if (first_bad >= 0) {
+        delete p;
+        if (bad_block) *bad_block = first_bad;
+        return fail(c, GPRF_NOT_PD, "predictor build: the kernel matrix of block " + std::to_string(first_bad) +
+                                        " is not positive definite");
+    }
+    DevBuf<PredGather> d_gl;
+    hipError_t e = hipSuccess;
+    if (e == hipSuccess) e = p->W.reserve(std::max<int64_t>(mat, 1), 1.0);
+    if (e == hipSuccess) e = p->A.reserve(std::max<int64_t>(rows, 1) * YPAD, 1.0);
+    if (e == hipSuccess) e = p->X.reserve(std::max<int64_t>(rows, 1) * p->rs, 1.0);
+    if (e == hipSuccess) e = d_gl.reserve(std::max<size_t>(gl.size(), 1), 1.0);
+    if (e == hipSuccess && !gl.empty())
+        e = hipMemcpy(d_gl.p, gl.data(), gl.size() * sizeof(PredGather), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) {
+        launch_pred_gather(d_gl.p, (int)gl.size(), c->d_W.p, c->d_At.p, c->d_Xu.p, p->rs, c->dy, p->W.p, p->A.p, p->X.p, max_m,
+                           c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    d_gl.release();
+    if (e != hipSuccess) {
+        (void)gprf_predictor_destroy(p);
+        return fail(c, GPRF_ERR_HIP, std::string("predictor build: ") + hipGetErrorString(e));
+    }
+    *out = p;
+    return GPRF_OK;
+}
+
+int gprf_predictor_destroy(gprf_predictor *p) {
+    if (!p) return GPRF_OK;
+    (void)hipSetDevice(p->device);
+    if (p->stream) { (void)hipStreamSynchronize(p->stream); (void)hipStreamDestroy(p->stream); }
+    p->W.release(); p->A.release(); p->X.release(); p->tab.release();
+    p->h_tab.release(); p->h_res.release(); p->h_status.release();
+    p->Kt.release(); p->V.release(); p->C.release(); p->Mn.release(); p->ws.release();
+    delete p;
+    return GPRF_OK;
+}
+
+const char *gprf_predictor_last_error(const gprf_predictor *p) { return p ? p->err.c_str() : ""; }
+
+int gprf_predict(gprf_predictor *p, int32_t n_test, const double *Xs, int32_t n_groups, const int64_t *group_ptr,
+                 const int32_t *group_rows, const int64_t *src_ptr, const int32_t *src_blocks, const double *prior_theta,
+                 int32_t n_prior, double test_noise_var, double *mean_out, double *cov_out, int32_t *bad_group) {
+    if (bad_group) *bad_group = -1;
+    if (!p) return GPRF_ERR_ARG;
+    if (n_test < 0 || n_groups < 0 || (n_test > 0 && !Xs) || !group_ptr || !src_ptr || !prior_theta)
+        return pfail(p, GPRF_ERR_ARG, "gprf_predict: missing argument");
+    if (n_prior != 1 + p->ndfn) return pfail(p, GPRF_ERR_ARG, "gprf_predict: prior_theta must be [signal_var, dfn_params...]");
+    if (!(test_noise_var >= 0.0)) return pfail(p, GPRF_ERR_ARG, "gprf_predict: test_noise_var must be >= 0");
+    if (group_ptr[0] != 0 || src_ptr[0] != 0) return pfail(p, GPRF_ERR_ARG, "gprf_predict: CSR pointers must start at 0");
+    if ((group_ptr[n_groups] > 0 && !group_rows) || (src_ptr[n_groups] > 0 && !src_blocks))
+        return pfail(p, GPRF_ERR_ARG, "gprf_predict: missing group_rows / src_blocks");
+    for (int64_t k = 0; k < src_ptr[n_groups]; ++k)
+        if (src_blocks[k] < 0 || src_blocks[k] >= p->n_blocks) return pfail(p, GPRF_ERR_ARG, "gprf_predict: source block out of range");
+    const int rs = p->rs, dy = p->dy;
+    // groups, tasks, work items, offsets (host bookkeeping, O(tasks))
+    std::vector<PredTask> tasks;
+    std::vector<PredGroup> groups;
+    std::vector<int4> items_k, items_v, items_c;
+    std::vector<double> xs;
+    int64_t v_tot = 0, c_tot = 0, mn_tot = 0, ws_tot = 0, mean_tot = 0, cov_tot = 0, xs_rows = 0;
+    std::vector<char> seen(p->n_blocks, 0);
+    for (int g = 0; g < n_groups; ++g) {
+        const int64_t r0 = group_ptr[g], r1 = group_ptr[g + 1];
+        if (r1 < r0) return pfail(p, GPRF_ERR_ARG, "gprf_predict: group_ptr must not decrease");
+        const int t = (int)(r1 - r0);
+        if (t > PRED_MAX_T)
+            return pfail(p, GPRF_ERR_ARG, "gprf_predict: group " + std::to_string(g) + " has " + std::to_string(t) +
+                                              " test points; at most " + std::to_string(PRED_MAX_T) + " per group");
+        if (src_ptr[g + 1] < src_ptr[g]) return pfail(p, GPRF_ERR_ARG, "gprf_predict: src_ptr must not decrease");
+        if (t == 0) continue;
+        const int tp = pad16(t);
+        // test point records (the gathered form of the training points, k_scatter_x), padding rows = the group's first point
+        for (int i = 0; i < tp; ++i) {
+            const int32_t row = group_rows[r0 + (i < t ? i : 0)];
+            if (row < 0 || row >= n_test) return pfail(p, GPRF_ERR_ARG, "gprf_predict: test row out of range");
+            const double *x = Xs + (size_t)row * p->dx;
+            double rec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (p->dist_id == GPRF_DIST_LLD) {
+                const double hl = x[1] * (M_PI / 180.0) / 2.0, hn = x[0] * (M_PI / 180.0) / 2.0;
+                rec[0] = std::sin(hl); rec[1] = std::cos(hl); rec[2] = std::sin(hn); rec[3] = std::cos(hn); rec[4] = x[2];
+            } else {
+                for (int d = 0; d < p->dx; ++d) rec[d] = x[d];
+            }
+            xs.insert(xs.end(), rec, rec + rs);
+        }
+        PredGroup gr{t, tp, (int32_t)xs_rows, (int32_t)tasks.size(), 0, 0, ws_tot, mean_tot, cov_tot};
+        for (int64_t k = src_ptr[g]; k < src_ptr[g + 1]; ++k) {
+            const int b = src_blocks[k];
+            if (seen[b] || p->b_m[b] == 0) continue;      // (a set, gprf.py:634-640; an empty block contributes nothing)
+            seen[b] = 1;
+            const int m = p->b_m[b], mp = pad16(m);
+            const int ti = (int)tasks.size();
+            tasks.push_back(PredTask{(int32_t)groups.size(), t, tp, m, mp, (int32_t)xs_rows, p->b_row[b], 0, p->b_mat[b], v_tot,
+                                     c_tot, mn_tot});
+            v_tot += (int64_t)mp * tp; c_tot += (int64_t)tp * tp; mn_tot += (int64_t)tp * YPAD;
+            for (int s = 0; s < tp / 16; ++s) {
+                items_k.push_back(make_int4(ti, s, 0, 0));
+                for (int r = 0; r <= mp / 16; ++r) items_v.push_back(make_int4(ti, s, r, 0));
+                for (int J = 0; J <= s; ++J) items_c.push_back(make_int4(ti, s, J, 0));
+            }
+        }
+        for (int64_t k = src_ptr[g]; k < src_ptr[g + 1]; ++k) seen[src_blocks[k]] = 0;
+        gr.n_task = (int32_t)tasks.size() - gr.task0;
+        groups.push_back(gr);
+        xs_rows += tp;
+        ws_tot += 3 * (int64_t)tp * tp + (int64_t)tp * YPAD;
+        mean_tot += (int64_t)t * dy; cov_tot += (int64_t)t * t;
+    }
+    if (groups.empty()) return GPRF_OK;
+    if ((int64_t)items_v.size() > INT32_MAX / 2 || (int64_t)items_k.size() > INT32_MAX / 2 || (int64_t)items_c.size() > INT32_MAX / 2)
+        return pfail(p, GPRF_ERR_ARG, "gprf_predict: too many work items");
+    if (!mean_out || !cov_out) return pfail(p, GPRF_ERR_ARG, "gprf_predict: missing output");
+    PHIP_TRY(p, hipSetDevice(p->device));
+    // one staged upload: tasks | groups | items_k | items_v | items_c | records
+    const size_t o_g = align16(tasks.size() * sizeof(PredTask));
+    const size_t o_ik = o_g + align16(groups.size() * sizeof(PredGroup));
+    const size_t o_iv = o_ik + align16(items_k.size() * sizeof(int4));
+    const size_t o_ic = o_iv + align16(items_v.size() * sizeof(int4));
+    const size_t o_x = o_ic + align16(items_c.size() * sizeof(int4));
+    const size_t tab_bytes = align16(o_x + xs.size() * sizeof(double));
+    PHIP_TRY(p, p->h_tab.reserve(tab_bytes));
+    PHIP_TRY(p, p->h_res.reserve((size_t)(mean_tot + cov_tot)));
+    PHIP_TRY(p, p->h_status.reserve(groups.size()));
+    char *h_tab = p->h_tab.p;
+    if (!tasks.empty()) memcpy(h_tab, tasks.data(), tasks.size() * sizeof(PredTask));
+    memcpy(h_tab + o_g, groups.data(), groups.size() * sizeof(PredGroup));
+    if (!items_k.empty()) memcpy(h_tab + o_ik, items_k.data(), items_k.size() * sizeof(int4));
+    if (!items_v.empty()) memcpy(h_tab + o_iv, items_v.data(), items_v.size() * sizeof(int4));
+    if (!items_c.empty()) memcpy(h_tab + o_ic, items_c.data(), items_c.size() * sizeof(int4));
+    memcpy(h_tab + o_x, xs.data(), xs.size() * sizeof(double));
+    PHIP_TRY(p, p->tab.reserve(tab_bytes));
+    PHIP_TRY(p, p->Kt.reserve(std::max<int64_t>(v_tot, 1)));
+    PHIP_TRY(p, p->V.reserve(std::max<int64_t>(v_tot, 1)));
+    PHIP_TRY(p, p->C.reserve(std::max<int64_t>(c_tot, 1)));
+    PHIP_TRY(p, p->Mn.reserve(std::max<int64_t>(mn_tot, 1)));
+    PHIP_TRY(p, p->ws.reserve(std::max<int64_t>(ws_tot, 1)));
+    PredArgs a;
+    a.tasks = (const PredTask *)p->tab.p;
+    a.groups = (const PredGroup *)(p->tab.p + o_g);
+    a.items_k = (const int4 *)(p->tab.p + o_ik);
+    a.items_v = (const int4 *)(p->tab.p + o_iv);
+    a.items_c = (const int4 *)(p->tab.p + o_ic);
+    a.pW = p->W.p; a.pA = p->A.p; a.pX = p->X.p;
+    a.xs = (const double *)(p->tab.p + o_x);
+    a.Kt = p->Kt.p; a.V = p->V.p; a.C = p->C.p; a.Mn = p->Mn.p; a.ws = p->ws.p;
+    a.mean_out = p->h_res.d; a.cov_out = p->h_res.d + mean_tot; a.status = p->h_status.d;
+    a.kp = p->kp;
+    a.kp_prior = p->kp;
+    a.kp_prior.sv = prior_theta[0];
+    for (int i = 0; i < 3; ++i) a.kp_prior.ls[i] = (i < p->ndfn) ? prior_theta[1 + i] : 1.0;
+    for (int i = 0; i < 3; ++i) a.kp_prior.inv_ls[i] = 1.0 / a.kp_prior.ls[i];
+    a.test_nv = test_noise_var;
+    a.dy = dy;
+    // (no copy command: the tables go up by k_pred_stage, the results come down as k_pred_fuse's stores into pinned memory)
+    launch_predict(p->dist_id, a, p->h_tab.d, tab_bytes, (int)items_k.size(), (int)items_v.size(), (int)items_c.size(),
+                   (int)groups.size(), p->stream);
+    PHIP_TRY(p, hipGetLastError());
+    PHIP_TRY(p, hipStreamSynchronize(p->stream));
+    memcpy(mean_out, p->h_res.p, (size_t)mean_tot * sizeof(double));
+    memcpy(cov_out, p->h_res.p + mean_tot, (size_t)cov_tot * sizeof(double));
+    const int32_t *st = p->h_status.p;
+    // (group indices of the caller: the k-th non-empty group)
+    for (size_t k = 0, g = 0; g < (size_t)n_groups; ++g) {
+        if (group_ptr[g + 1] == group_ptr[g]) continue;
+        if (st[k++]) {
+            if (bad_group) *bad_group = (int32_t)g;
+            return pfail(p, GPRF_NOT_PD, "gprf_predict: a covariance of group " + std::to_string(g) + " is not positive definite");
+        }
+    }
+    return GPRF_OK;
+}
+
+}  // extern "C"

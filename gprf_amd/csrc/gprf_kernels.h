@@ -251,4 +251,34 @@ void launch_pair_max(int dist_id, int kern_id, const double *X, int dx, const in
                      const int32_t *cand, int n_cand, const KParams &kp, double thr, int want_max, int32_t *keep,
                      double *max_out, hipStream_t s);
 
+
+// ---- prediction (gprf_predict.hip; GPRF.train_predictor / predict, gprf.py:593-672) ----
+constexpr int PRED_MAX_T = 512;   // test points per group
+// one unary unit's snapshot: W (mp x mp at src_mat in the W pool), At / coordinate rows at src_row -> the predictor's pools
+struct PredGather { int64_t src_mat, dst_mat; int32_t src_row, dst_row, m, pad; };
+// one (group, source block) pair; t / tp: the group's test points (tp = t rounded up to 16), m / mp: the block's points
+struct PredTask {
+    int32_t g, t, tp, m, mp, xs_row, b_row, pad;
+    int64_t b_mat, v_off, c_off, mean_off;
+};
+struct PredGroup { int32_t t, tp, xs_row, task0, n_task, pad; int64_t ws_off, mean_off, cov_off; };
+struct PredArgs {
+    const PredTask *tasks;
+    const PredGroup *groups;
+    const int4 *items_k, *items_v, *items_c;   // (task, strip) / (task, strip, row block) / (task, tile row, tile column)
+    const double *pW, *pA, *pX;         // the predictor's pools: W, alpha (YPAD per row), point records
+    const double *xs;                   // test point records, groups' rows padded to tp
+    double *Kt, *V, *C, *Mn, *ws;       // per task: K*^T and V (mp x tp), cov (tp x tp), mean (tp x YPAD); per group: workspace
+    double *mean_out, *cov_out;         // pinned host memory (the device's view of it)
+    int32_t *status;                    // ... per group: 1 = a matrix that had to be inverted was not positive definite
+    KParams kp, kp_prior;
+    double test_nv;
+    int dy;
+};
+void launch_pred_gather(const PredGather *gl, int n, const double *W, const double *At, const double *Xu, int rs, int dy,
+                        double *pW, double *pA, double *pX, int max_m, hipStream_t s);
+// tab_src: the call's tables in pinned host memory (device view), tab_bytes (a multiple of 16) of them, copied to a.tasks first
+void launch_predict(int dist_id, const PredArgs &a, const void *tab_src, size_t tab_bytes, int n_items_k, int n_items_v,
+                    int n_items_c, int n_groups, hipStream_t s);
+
 }  // namespace gprf

@@ -81,6 +81,7 @@ class GPRF(object):
                                   device=device, devices=devices)
         self._shard = (int(shard[0]), int(shard[1])) if shard is not None else (0, 1)
         self._group, self._reduce, self._dist_eval = group, bool(reduce), None
+        self._multi = devices is not None
         if shard is not None:
             self._ctx.set_shard(*self._shard)
         self._ctx.set_Y(Y)
@@ -428,6 +429,24 @@ class GPRF(object):
 
         (rc, ll, gX, gC), _ = jitter_schedule(ev, bad, n_units, diag_mean, self._jitter)
         return rc, ll, gX, gC
+
+    # ------------------------------------------------------------------ prediction
+    def train_predictor(self, test_cov=None, Y=None):
+        """gprf.py:593-672 -> a ``predict.Predictor``, callable as ``predict(Xstar, test_noise_var=0.0, local=False) ->
+        (mean, cov)``, with ``predict_blocks`` / ``close``.  A snapshot of the model as it stands: later update_X /
+        update_covs / llgrad calls do not change it.  ``Y`` replaces the training targets the block alphas are made from;
+        ``test_cov`` is the prior covariance of the test points (default: the model's)."""
+        if self._multi or self._shard[1] > 1:
+            raise NotImplementedError("train_predictor on a sharded / multi-device GPRF: build the predictor from a "
+                                      "single-device GPRF")
+        from .predict import Predictor
+        self.block_idxs                          # (runs a pending re-blocking)
+        self._push_blocks()
+        self._push_neighbors(self.neighbors)
+        if self._jitter is not None:             # (the reference inverts the plain K, gprf.py:612-613)
+            self._jitter = None
+            self._ctx.set_unit_jitter(None)
+        return Predictor(self, test_cov=test_cov, Y=Y)
 
     # reference attribute names some callers read
     @property

@@ -278,6 +278,33 @@ int gprf_set_stream_pipelines(gprf_ctx *ctx, int32_t enable);
 int gprf_get_timing(gprf_ctx *ctx, int32_t n, double *ms_out);
 #define GPRF_N_STAGES 7
 
+/* ---- Prediction: GPRF.train_predictor(test_cov=None, Y=None) -> predict(Xstar, test_noise_var=0.0, local=False)
+ * (gprf.py:593-672), for the stationary model, with the three fixes its stationary branch needs: K = the training kernel with
+ * noise_var on the diagonal (gprf.py:333-343), the messages use the model's own covariance, nv = noise_var.
+ * gprf_predictor_create runs the pipeline up to At on X (n x dx) and the context's blocks / theta / Y and keeps a SNAPSHOT of
+ * every block's W = U^-T (K^-1 = W^T W), alpha = K^-1 Y[block] and point records: later calls on the context do not change
+ * it.  Y (may be NULL): n x dy targets used for the alphas instead of the context's (whose Y is left as it was).  A block whose
+ * kernel matrix is not positive definite fails the build: GPRF_NOT_PD, *bad_block = the lowest such block, else -1.  Plain
+ * contexts only: a multi-device group or a sharded context returns GPRF_ERR_STATE.  Errors: gprf_last_error(ctx).
+ * gprf_predict evaluates n_groups independent predictions in one call (the number of kernel launches does not depend on
+ * n_groups).  Group g is the test rows group_rows[group_ptr[g] .. group_ptr[g+1]) of Xs (n_test x dx), at most 512 of them
+ * (more: GPRF_ERR_ARG); its sources are the blocks src_blocks[src_ptr[g] .. src_ptr[g+1]) (repeats count once, empty blocks
+ * contribute nothing; no source at all gives the prior).  For each group, with k the model's covariance, k_test the prior's
+ * (prior_theta = [signal_var, dfn_params...]; the distance and kernel are the model's: test_cov of another form is not
+ * supported) and Kss = k(X*, X*) (+ noise_var I when test_noise_var > 0):
+ *     P = inv(k_test(X*, X*) + test_noise_var I) + sum_i (inv(cov_i) - inv(Kss)),   b = sum_i inv(cov_i) mean_i,
+ *     mean_i = k(X*, X_i) alpha_i,   cov_i = Kss - k(X*, X_i) K_i^-1 k(X_i, X*),   cov = inv(P),   mean = cov b,
+ * every inverse by Cholesky.  Outputs, groups in order (empty groups take no space): mean_out t x dy row-major each,
+ * cov_out t x t row-major each.  A matrix that is not positive definite: GPRF_NOT_PD, *bad_group = its group.  Errors:
+ * gprf_predictor_last_error. */
+typedef struct gprf_predictor gprf_predictor;
+int gprf_predictor_create(gprf_ctx *ctx, const double *X, const double *Y, gprf_predictor **out, int32_t *bad_block);
+int gprf_predictor_destroy(gprf_predictor *p);
+const char *gprf_predictor_last_error(const gprf_predictor *p);
+int gprf_predict(gprf_predictor *p, int32_t n_test, const double *Xs, int32_t n_groups, const int64_t *group_ptr,
+                 const int32_t *group_rows, const int64_t *src_ptr, const int32_t *src_blocks, const double *prior_theta,
+                 int32_t n_prior, double test_noise_var, double *mean_out, double *cov_out, int32_t *bad_group);
+
 /* Per-stage parity hooks (tests only): after an evaluation, copy one local unit's intermediates to the
  * host.  what: 0 the factor pool (mp x mp, upper triangle = Cholesky factor U, K = U^T U; the strictly-lower
  * part is unspecified) — or, after a fill-only gprf_debug_run (stop_after = 0), the K pool (64x64 blocks
