@@ -29,6 +29,7 @@ SIGNATURES = {
     "gprf_destroy": (ctypes.c_int, [_vp]),
     "gprf_last_error": (ctypes.c_char_p, [_vp]),
     "gprf_set_Y": (ctypes.c_int, [_vp, _dp]),
+    "gprf_set_YY": (ctypes.c_int, [_vp, _dp, _i32]),
     "gprf_set_theta": (ctypes.c_int, [_vp, _dp, _i32]),
     "gprf_set_blocks": (ctypes.c_int, [_vp, _i32, _i64p, _i32p]),
     "gprf_set_neighbors": (ctypes.c_int, [_vp, _i32, _i32p]),
@@ -249,8 +250,15 @@ class Context(object):
 
     def set_Y(self, Y):
         Y = np.ascontiguousarray(Y, dtype=np.float64)
-        assert Y.shape == (self.n, self.dy)
+        if self.dy:                      # (a kernelized context, dy = 0, refuses the call itself)
+            assert Y.shape == (self.n, self.dy)
         self._check(self.lib.gprf_set_Y(self.h, dptr(Y)), "gprf_set_Y")
+
+    def set_YY(self, YY, dy):
+        """kernelized context (created with dy = 0): the n x n Gram matrix of the outputs and their dimension dy"""
+        YY = np.ascontiguousarray(YY, dtype=np.float64)
+        assert YY.shape == (self.n, self.n)
+        self._check(self.lib.gprf_set_YY(self.h, dptr(YY), int(dy)), "gprf_set_YY")
 
     def set_theta(self, theta):
         theta = np.ascontiguousarray(theta, dtype=np.float64).ravel()

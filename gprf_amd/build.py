@@ -10,7 +10,7 @@ LIB = os.environ.get("GPRF_LIB") or os.path.join(HERE, "libgprf_hip.so")
 # side by side and a kernel variant recompiles one of them)
 # (slowest first: they start first)
 SOURCES = ["gprf_solve_wide32.hip", "gprf_solve_wide.hip", "gprf_solve.hip", "gprf_solve_class.hip", "gprf_potrf.hip", "gprf_mgrad.hip", "gprf_big.hip",
-           "gprf_fill.hip", "gprf_tables.hip", "gprf_predict.hip", "gprf_capi.hip"]
+           "gprf_fill.hip", "gprf_tables.hip", "gprf_predict.hip", "gprf_kernelized.hip", "gprf_capi.hip"]
 HEADERS = ["gprf_kernels.h", "gprf_dev.h", "gprf_solve_panel.h", os.path.join("..", "..", "include", "gprf_hip.h")]
 
 

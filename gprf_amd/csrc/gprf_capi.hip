@@ -92,6 +92,13 @@ struct gprf_ctx {
     bool side_values = false;             // the device supports hipStreamWaitValue32
     std::string err;
 
+    // kernelized observations (gprf_create with dy = 0, gprf_set_YY): the outputs through their n x n Gram matrix d_YY; the
+    // evaluation pipeline runs as a dy = 1 context over zero outputs (d_Y) up to W, then gprf_kernelized.hip; kz_dy = the dy of
+    // the log-likelihood and of M = P YYu P - dy P
+    bool kernelized = false;
+    int kz_dy = 0;
+    DevBuf<double> d_YY;
+
     // host-side model state (what the reference keeps on the GPRF object)
     std::vector<double> theta;
     bool have_Y = false, have_theta = false, have_blocks = false;
@@ -588,7 +595,7 @@ int check_ready(gprf_ctx *c) {
         if (rc != GPRF_OK) c->err = c->kids[0]->err;
         return rc;
     }
-    if (!c->have_Y) return fail(c, GPRF_ERR_STATE, "gprf_set_Y has not been called");
+    if (!c->have_Y) return fail(c, GPRF_ERR_STATE, c->kernelized ? "gprf_set_YY has not been called" : "gprf_set_Y has not been called");
     if (!c->have_theta) return fail(c, GPRF_ERR_STATE, "gprf_set_theta has not been called");
     if (!c->have_blocks) return fail(c, GPRF_ERR_STATE, "gprf_set_blocks has not been called");
     return GPRF_OK;
@@ -737,7 +744,8 @@ int enqueue_eval(gprf_ctx *c, const double *d_X, int want_gx, int want_gc, doubl
         // device-resident figure — share a few hardware queues between their side streams, and four more kernels on each
         // cost that form 12 %)
         const bool plain = !beside && !tm && (s == c->stream || c->caller_pipelines) && !(diag("pipe", PIPE_DEFAULT_PCT) > 0 && diag("pipe", PIPE_DEFAULT_PCT) < 100);
-        const int want_stages = !plain ? 0 : (do_grad ? 3 : (stop_after >= 3 ? 2 : (stop_after >= 2 ? 1 : 0)));
+        int want_stages = !plain ? 0 : (do_grad ? 3 : (stop_after >= 3 ? 2 : (stop_after >= 2 ? 1 : 0)));
+        if (c->kernelized && want_stages > 1) want_stages = 1;      // (the kernelized products follow the substitution)
         // (the zero-copy, polled host path on the library's own stream may continue on whichever queue carries the longer
         // pipeline: the completion word is polled, nothing is waited for on a stream, and the next evaluation is not enqueued
         // before this one has been seen to finish)
@@ -763,7 +771,7 @@ int enqueue_eval(gprf_ctx *c, const double *d_X, int want_gx, int want_gc, doubl
     // queue's workgroups of the same kernel and the first part's next stage starts no sooner than before; and two half-size
     // launches lose the launch-wide longest-workgroup-first order that shortened these tails in round 3.
     const int pipe_pct = diag("pipe", PIPE_DEFAULT_PCT);
-    const bool pipe = pipe_pct > 0 && pipe_pct < 100 && !tm && stop_after >= 5 && do_grad && c->stream3 && c->side_values &&
+    const bool pipe = !c->kernelized && pipe_pct > 0 && pipe_pct < 100 && !tm && stop_after >= 5 && do_grad && c->stream3 && c->side_values &&
                       s == c->stream && !potrf_tool_env() && ut.max_T <= SMALL_MAX_T && ut.n_ids >= PIPE_MIN_UNITS;
     if (pipe) {
         int nA = ((ut.n_ids * pipe_pct / 100) + 7) & ~7;
@@ -802,16 +810,25 @@ int enqueue_eval(gprf_ctx *c, const double *d_X, int want_gx, int want_gc, doubl
         }
     }
     mark();
+    if (c->kernelized) {
+        // tr(P YYu) (the ll term) and M = P YYu P - dy P in place of At and the chunk loop of k_mgrad
+        if (stop_after >= 3) launch_kz_products(ut, pl, c->d_YY.p, c->n, (double)c->kz_dy, do_grad, s);
+        mark();
+        if (do_grad) launch_grad_from_M(c->dist_id, c->kern_id, ut, pl, kp, want_gc, s);
+    } else {
     if (stop_after >= 3 && solved < 2) launch_at(ut, pl, s);
     mark();
     if (do_grad && solved < 3) launch_grad(c->dist_id, c->kern_id, ut, pl, kp, want_gc, !gen, s);      // (re-evaluates k whenever K was generated for some units)
     }
+    }
+    KParams kp_ll = kp;                   // the dy of the log-likelihood (k_gx_finalize, k_assemble)
+    if (c->kernelized) kp_ll.dy = c->kz_dy;
     if (do_grad) {
         // k_gx_finalize is a launch of its own for sums the assembly can do on the way (10 us of a 430 us evaluation) —
         // up to GX_FOLD_MAX_UNITS units; beyond that the assembly's single summing workgroup would walk every unit's
         // partials itself (C4: 106 us against 20).  The per-unit gradient (gprf_debug_fetch) is then made on demand.
         fold_gx = diag("gx_fold", 1) != 0 && stop_after >= 5 && c->n_local <= GX_FOLD_MAX_UNITS;
-        if (!fold_gx) launch_gx_finalize(ut, pl, kp, want_gc, s);
+        if (!fold_gx) launch_gx_finalize(ut, pl, kp_ll, want_gc, s);
         c->gxu_pending = fold_gx;
         c->gxu_want_gc = want_gc;
     }
@@ -833,7 +850,7 @@ int enqueue_eval(gprf_ctx *c, const double *d_X, int want_gx, int want_gc, doubl
     c->poll_pending = false;
     const bool poll = host_io && stop_after >= 5 && c->spin && c->h_done.p && !(host_io == 2 && c->io_mode == 1);
     if (poll) c->done_seq = c->done_seq >= 0x3fffffff ? 1 : c->done_seq + 1;
-    if (stop_after >= 5) launch_assemble(ut, pl, at, kp, c->n, want_gx, want_gc, d_out, (do_grad && !fold_gx) ? 1 : 0, ob, s);
+    if (stop_after >= 5) launch_assemble(ut, pl, at, kp_ll, c->n, want_gx, want_gc, d_out, (do_grad && !fold_gx) ? 1 : 0, ob, s);
     mark();
     if (objective) {
         const double nel = (double)c->n * c->dx;
@@ -1175,8 +1192,11 @@ int gprf_create(gprf_ctx **out, int32_t n, int32_t dx, int32_t dy, int32_t dist_
     *out = nullptr;
     g_create_err.clear();
     char why[200];
+    // dy = 0: a kernelized context (observations through their Gram matrix, gprf_set_YY)
+    const bool kernelized = dy == 0;
+    if (kernelized) dy = 1;
     if (n < 0 || dy < 1 || dy > YPAD) {
-        snprintf(why, sizeof why, "n = %d, dy = %d: need n >= 0 and 1 <= dy <= %d", n, dy, YPAD);
+        snprintf(why, sizeof why, "n = %d, dy = %d: need n >= 0 and 1 <= dy <= %d (or dy = 0: kernelized)", n, dy, YPAD);
         return create_fail(GPRF_ERR_ARG, why);
     }
     bool se = (dist_id == GPRF_DIST_EUCLIDEAN && kern_id == GPRF_KERN_SE);
@@ -1229,6 +1249,14 @@ int gprf_create(gprf_ctx **out, int32_t n, int32_t dx, int32_t dy, int32_t dist_
         return create_fail(GPRF_ERR_HIP, "out of memory for the context's resident buffers");
     }
     c->h_done.p[0] = 0;
+    if (kernelized) {
+        c->kernelized = true;
+        // the pipeline's right-hand side: one column of zeros (Z = At = 0; the kernelized products replace what they fed)
+        if (hipMemset(c->d_Y.p, 0, ((size_t)n + 1) * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+            gprf_destroy(c);
+            return create_fail(GPRF_ERR_HIP, "could not clear the kernelized context's right-hand side");
+        }
+    }
     if (const char *e = getenv("GPRF_SYNC")) c->spin = !(e[0] == 'b');
     if (const char *e = getenv("GPRF_IO_MODE")) c->io_mode = (e[0] == '1' || e[0] == '2') ? e[0] - '0' : 0;
     *out = c;
@@ -1238,6 +1266,11 @@ int gprf_create(gprf_ctx **out, int32_t n, int32_t dx, int32_t dy, int32_t dist_
 int gprf_create_multi(gprf_ctx **out, int32_t n, int32_t dx, int32_t dy, int32_t dist_id, int32_t kern_id,
                       int32_t n_devices, const int32_t *devices) {
     if (!out) return GPRF_ERR_ARG;
+    if (dy == 0) {
+        *out = nullptr;
+        g_create_err.clear();
+        return create_fail(GPRF_ERR_STATE, "a kernelized context (dy = 0) is single-device: gprf_create_multi refuses it");
+    }
     *out = nullptr;
     g_create_err.clear();
     if (n_devices < 1 || n_devices > 64 || !devices) return create_fail(GPRF_ERR_ARG, "1 <= n_devices <= 64 device ordinals");
@@ -1378,7 +1411,7 @@ int gprf_destroy(gprf_ctx *c) {
     if (c->slots_base) { if (c->slots_on_host) (void)hipHostFree(c->slots_base); else (void)hipFree(c->slots_base); }
     if (c->ev_last) (void)hipEventSynchronize(c->ev_last);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    c->d_X.release(); c->d_Y.release(); c->d_out.release(); c->d_tab.release(); c->h_tab.release();
+    c->d_X.release(); c->d_Y.release(); c->d_YY.release(); c->d_out.release(); c->d_tab.release(); c->h_tab.release();
     c->d_m.release(); c->d_rowoff.release(); c->d_offj.release(); c->d_upt.release(); c->d_assign.release();
     c->d_posb.release(); c->d_rank.release(); c->d_big_list.release(); c->d_small_list.release(); c->d_srec.release(); c->d_big_rec.release(); c->d_small_rec.release(); c->d_pe.release(); c->d_ebase.release(); c->d_einfo.release(); c->d_cnt.release(); c->d_matoff.release(); c->d_res.release();
     c->h_res.release(); c->h_up.release();
@@ -1411,11 +1444,33 @@ const char *gprf_last_error(const gprf_ctx *c) {
 
 int gprf_set_Y(gprf_ctx *c, const double *Y) {
     if (!c || !Y) return GPRF_ERR_ARG;
+    if (c->kernelized) return fail(c, GPRF_ERR_STATE, "a kernelized context takes its observations through gprf_set_YY");
     GROUP_FORWARD(c, gprf_set_Y(k, Y))
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->ev_last) HIP_TRY(c, hipEventSynchronize(c->ev_last));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(c->d_Y.p, Y, (size_t)c->n * c->dy * sizeof(double), hipMemcpyHostToDevice));
+    c->have_Y = true;
+    return GPRF_OK;
+}
+
+int gprf_set_YY(gprf_ctx *c, const double *YY, int32_t dy) {
+    if (!c || !YY) return GPRF_ERR_ARG;
+    if (!c->kernelized) return fail(c, GPRF_ERR_STATE, "gprf_set_YY needs a kernelized context (gprf_create with dy = 0)");
+    if (dy < 1) return fail(c, GPRF_ERR_ARG, "gprf_set_YY: dy must be >= 1");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->ev_last) HIP_TRY(c, hipEventSynchronize(c->ev_last));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t nn = (size_t)c->n * (size_t)c->n;
+    if (c->d_YY.reserve(nn + 1, 1.0) != hipSuccess) {
+        (void)hipGetLastError();
+        char buf[200];
+        snprintf(buf, sizeof buf, "gprf_set_YY: could not allocate the n x n Gram matrix (n = %d: %zu bytes)", c->n,
+                 nn * sizeof(double));
+        return fail(c, GPRF_ERR_HIP, buf);
+    }
+    HIP_TRY(c, hipMemcpy(c->d_YY.p, YY, nn * sizeof(double), hipMemcpyHostToDevice));
+    c->kz_dy = dy;
     c->have_Y = true;
     return GPRF_OK;
 }
@@ -1782,6 +1837,7 @@ int gprf_partition_units(int32_t n_units, const int32_t *m, int32_t dy, int32_t 
 int gprf_set_shard(gprf_ctx *c, int32_t rank, int32_t world) {
     if (!c || world < 1 || rank < 0 || rank >= world) return GPRF_ERR_ARG;
     GROUP_REFUSE(c, "gprf_set_shard")
+    if (c->kernelized) return fail(c, GPRF_ERR_STATE, "gprf_set_shard: a kernelized context is not sharded");
     c->rank = rank;
     c->world = world;
     c->static_dirty = true;
@@ -1810,6 +1866,7 @@ int gprf_set_unit_jitter(gprf_ctx *c, int32_t n_units, const double *jitter) {
 int gprf_eval_device(gprf_ctx *c, const double *d_X, int32_t want_gradX, int32_t want_gradC, double *d_out,
                      void *stream) {
     GROUP_REFUSE(c, "gprf_eval_device")
+    if (c && c->kernelized) return fail(c, GPRF_ERR_STATE, "gprf_eval_device is not available on a kernelized context");
     int rc = check_ready(c);
     if (rc != GPRF_OK) return rc;
     if (!d_X || !d_out) return GPRF_ERR_ARG;
@@ -1821,6 +1878,7 @@ int gprf_eval_device(gprf_ctx *c, const double *d_X, int32_t want_gradX, int32_t
 int gprf_update_eval_device(gprf_ctx *c, const double *d_X, int32_t want_gradX, int32_t want_gradC, double *d_out,
                             void *stream) {
     GROUP_REFUSE(c, "gprf_update_eval_device")
+    if (c && c->kernelized) return fail(c, GPRF_ERR_STATE, "gprf_update_eval_device is not available on a kernelized context");
     int rc = check_ready(c);
     if (rc != GPRF_OK) return rc;
     if (!d_X || !d_out) return GPRF_ERR_ARG;
@@ -2009,6 +2067,7 @@ int gprf_objective(gprf_ctx *c, const double *z, int32_t nz, const double *X_fix
 int gprf_objective_device(gprf_ctx *c, const double *d_X, int32_t want_gradX, int32_t want_gradC, double *d_out,
                           void *stream, int32_t reblock) {
     GROUP_REFUSE(c, "gprf_objective_device")
+    if (c && c->kernelized) return fail(c, GPRF_ERR_STATE, "gprf_objective_device is not available on a kernelized context");
     int rc = check_ready(c);
     if (rc != GPRF_OK) return rc;
     if (!d_X || !d_out) return GPRF_ERR_ARG;
@@ -2292,6 +2351,7 @@ int gprf_predictor_create(gprf_ctx *c, const double *X, const double *Y, gprf_pr
     if (bad_block) *bad_block = -1;
     if (!c || !X || !out) return GPRF_ERR_ARG;
     GROUP_REFUSE(c, "gprf_predictor_create")
+    if (c->kernelized) return fail(c, GPRF_ERR_STATE, "gprf_predictor_create needs the outputs Y: build it from a plain context");
     if (c->world > 1) return fail(c, GPRF_ERR_STATE, "gprf_predictor_create is not available on a sharded context");
     int rc = check_ready(c);
     if (rc != GPRF_OK) return rc;

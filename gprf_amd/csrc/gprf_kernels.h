@@ -239,6 +239,11 @@ void launch_at(const UnitTab &ut, const Pools &p, hipStream_t s);
 void launch_grad(int dist_id, int kern_id, const UnitTab &ut, const Pools &p, const KParams &kp, int want_gc,
                  bool have_K, hipStream_t s);
 void launch_gx_finalize(const UnitTab &ut, const Pools &p, const KParams &kp, int want_gc, hipStream_t s);
+// kernelized observations (gprf_kernelized.hip; gprf.py:674-736), behind the Cholesky and the substitution: per unit
+// tr(P YYu) into zzpart and — want_M — M = P YYu P - dy P into the unit's K region (the U region is scratch); YY: n x n
+void launch_kz_products(const UnitTab &ut, const Pools &p, const double *YY, int n, double dy, bool want_M, hipStream_t s);
+// ... then k_mgrad's reductions over that M, for units of every size
+void launch_grad_from_M(int dist_id, int kern_id, const UnitTab &ut, const Pools &p, const KParams &kp, int want_gc, hipStream_t s);
 void launch_assemble(const UnitTab &ut, const Pools &p, const AssembleTab &at, const KParams &kp, int n,
                      int want_gx, int want_gc, double *out, int usum_ok, const ObjTab &ob, hipStream_t s);
 void launch_finish(double *out, const ObjTab &ob, int nparts, double xp_const, double *extras, int32_t *flag, int32_t seq,

@@ -44,12 +44,15 @@ __device__ __forceinline__ double row16_sum(double v) {
 // BIG (round 5): the units of more than 1024 points only — their M tiles were made by k_big_gemm (mode 2, 128 x 128 tiles at
 // four times this kernel's flops per byte) and wait in the unit's region of the K pool: the chunk loop is skipped, the
 // accumulators are loaded, the reductions are the same code.  The plain instantiations leave those units alone.
-template <int DIST, int KERN, bool HAVEK, int FAST, bool BIG = false, int CLS = 0>
+// MEM (kernelized observations, gprf_kernelized.hip): the same loaded form for the units of EVERY size, walked like the plain
+// instantiations; M = P YYu P - dy P was written to the K pool by k_kz_gemm.
+template <int DIST, int KERN, bool HAVEK, int FAST, bool BIG = false, int CLS = 0, bool MEM = false>
 #ifndef GPRF_MGRAD_LLD_WPC
 #define GPRF_MGRAD_LLD_WPC 2
 #endif
 __global__ __launch_bounds__(256, (DIST == 0 && KERN == 0) ? (FAST ? 4 : 3) : GPRF_MGRAD_LLD_WPC) void k_mgrad(UnitTab ut, Pools pl, KParams kp, int want_gc, int part_major) {
     static_assert(!(BIG && HAVEK), "the big units' K region holds M: their kernel values are re-evaluated");
+    static_assert(!(MEM && (HAVEK || BIG || CLS != 0)), "the kernelized form: M in the K pool, launch-wide list");
     __shared__ double chunk[2][16 * G2_LD];
     // the coordinates (or lld records) of the I block's and the J block's points, fetched at kernel start so that the
     // reductions at the end find them in LDS instead of starting with exposed global loads
@@ -78,7 +81,7 @@ __global__ __launch_bounds__(256, (DIST == 0 && KERN == 0) ? (FAST ? 4 : 3) : GP
     int u = ur.u;
     int m = ur.m;
     int mp = pad16(m), T = mp >> 4;
-    if (BIG != (T > SMALL_MAX_T)) return;      // (uniform) the other instantiation's units
+    if (!MEM && BIG != (T > SMALL_MAX_T)) return;      // (uniform) the other instantiation's units
     int TB = (T + 3) >> 2;
     // block pair index -> (JB, IB >= JB), enumerated over the launch-wide TBm
     int JB = 0, rem = bp;
@@ -212,7 +215,7 @@ __global__ __launch_bounds__(256, (DIST == 0 && KERN == 0) ? (FAST ? 4 : 3) : GP
     // (bottom-left) block pair -> Pools::dbg[u][0..3] / [4..7]
     unsigned long long tm0 = __builtin_amdgcn_s_memtime();
 #endif
-    if constexpr (BIG) {
+    if constexpr (BIG || MEM) {
         const double *__restrict__ Mp = pl.K + ur.mat_off;
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj)
@@ -227,7 +230,7 @@ __global__ __launch_bounds__(256, (DIST == 0 && KERN == 0) ? (FAST ? 4 : 3) : GP
 #ifdef GPRF_PROFILE
     unsigned long long tm1 = __builtin_amdgcn_s_memtime();
 #endif
-    for (int c = 0; !BIG && c < nch; c += 2) {
+    for (int c = 0; !(BIG || MEM) && c < nch; c += 2) {
         step(c, pre0, true);
         if (c + 1 < nch) step(c + 1, pre1, false);
     }
@@ -879,6 +882,25 @@ void launch_grad(int dist_id, int kern_id, const UnitTab &ut, const Pools &p, co
     }
 }
 
+
+// kernelized observations: every unit's M waits in its K region (launch_kz_products); the reductions of k_mgrad alone, walked
+// like launch_grad's plain launch
+void launch_grad_from_M(int dist_id, int kern_id, const UnitTab &ut, const Pools &p, const KParams &kp, int want_gc, hipStream_t s) {
+    if (ut.n_ids == 0 || ut.max_T == 0) return;
+    const int TBm = (ut.max_T + 3) / 4, nbp = TBm * (TBm + 1) / 2;
+    const int G = (ut.n_launch > 2 * device_cus() || (dist_id == 1 && ut.n_launch > 128)) ? 64 : 0;
+    dim3 grid(G > 0 ? ((ut.n_ids + G - 1) / G) * G * nbp : xcd_grid(ut.n_ids, nbp));
+    UnitTab utp = ut;
+    utp.pm_group = G;
+    if (dist_id == 0 && kern_id == 0) {
+        const int fast = kp.dx <= 2 ? (want_gc ? 2 : 1) : 0;
+        if (fast == 1) hipLaunchKernelGGL((k_mgrad<0, 0, false, 1, false, 0, true>), grid, dim3(256), 0, s, utp, p, kp, want_gc, 1);
+        else if (fast == 2) hipLaunchKernelGGL((k_mgrad<0, 0, false, 2, false, 0, true>), grid, dim3(256), 0, s, utp, p, kp, want_gc, 1);
+        else hipLaunchKernelGGL((k_mgrad<0, 0, false, 0, false, 0, true>), grid, dim3(256), 0, s, utp, p, kp, want_gc, 1);
+    } else {
+        hipLaunchKernelGGL((k_mgrad<1, 1, false, 0, false, 0, true>), grid, dim3(256), 0, s, utp, p, kp, want_gc, 1);
+    }
+}
 
 void launch_assemble(const UnitTab &ut, const Pools &p, const AssembleTab &at, const KParams &kp, int n,
                      int want_gx, int want_gc, double *out, int usum_ok, const ObjTab &ob, hipStream_t s) {

@@ -39,8 +39,10 @@ class GPRF(object):
     def __init__(self, X, Y, block_fn, cov, noise_var, kernelized=False, dy=None,
                  neighbor_threshold=1e-3, nonstationary=False, nonstationary_prec=False,
                  block_idxs=None, neighbors=None, device=0, shard=None, group=None, reduce=True, devices=None):
-        """Arguments as gprf.py:85-87.  ``kernelized`` / ``nonstationary`` are dead or broken branches in
-        the reference (Appendix A.9/11) and are refused.  ``device`` = HIP device
+        """Arguments as gprf.py:85-87.  ``kernelized=True``: ``Y`` is the n x n Gram matrix ``YY`` of the outputs (exactly
+        symmetric) and ``dy`` (an integer >= 1, of any size) their dimension; every unit is then evaluated as
+        gaussian_llgrad_kernel (gprf.py:674-736), which the reference never reaches.  The ``nonstationary``
+        variants are broken branches in the reference and are refused.  ``device`` = HIP device
         ordinal.  ``shard`` = (rank, world): this object evaluates only its rank's share of the units and ``llgrad``
         all-reduces the partial sums over the torch.distributed ``group`` (one process per GPU; the counterpart of
         the reference's process-pool fan-out inside llgrad, gprf.py:218-233), so every rank returns the full result
@@ -48,17 +50,32 @@ class GPRF(object):
         (tests, callers that reduce themselves).  ``devices`` = a list of HIP device ordinals (or a count N = devices
         0..N-1): ONE process drives them all (gprf_create_multi): the units are sharded over the devices inside the
         library, partial sums meet on the first device — the reference's single-process driver needs no torchrun."""
-        if kernelized or nonstationary or nonstationary_prec:
-            raise NotImplementedError("kernelized / nonstationary GPRF variants are unreachable in the "
-                                      "reference (gprf.py:90-97,302) and are not provided")
+        if nonstationary or nonstationary_prec:
+            raise NotImplementedError("nonstationary GPRF variants are broken in the reference (gprf.py:90-97,302) and are "
+                                      "not provided")
+        if kernelized:
+            if shard is not None or devices is not None:
+                raise NotImplementedError("kernelized=True is single-device: shard= / devices= are not available")
+            if dy is None or isinstance(dy, (bool, np.bool_)) or not isinstance(dy, (int, np.integer)) or dy < 1:
+                raise ValueError("kernelized=True needs dy, the dimension of the outputs: an integer >= 1 (got %r)" % (dy,))
+            YY = np.ascontiguousarray(Y, dtype=np.float64)
+            if YY.shape != (X.shape[0], X.shape[0]):
+                raise ValueError("kernelized=True: YY must be n x n = %d x %d (got %s)" % (X.shape[0], X.shape[0], YY.shape))
+            if not np.array_equal(YY, YY.T):
+                raise ValueError("kernelized=True: YY must be exactly symmetric (np.array_equal(YY, YY.T)); "
+                                 "pass 0.5*(YY+YY.T)")
         if (cov.dfn_str, cov.wfn_str) not in SUPPORTED:
             raise ValueError("unsupported covariance (%s, %s)" % (cov.dfn_str, cov.wfn_str))
         if len(cov.wfn_params) != 1:
             raise ValueError('gradient computation currently assumes just a single scaling parameter for '
                              'weight function, but currently wfn_params=%s' % (cov.wfn_params,))  # gprf.py:369-370
         self.X = X
-        self.kernelized = False
-        self.Y = Y
+        self.kernelized = bool(kernelized)
+        if kernelized:
+            self.YY, self.dy = YY, int(dy)        # (as the reference: no self.Y, gprf.py:90-97)
+        else:
+            self.Y = Y
+        self._device = device
         self._block_idxs = None
         self._block_of = None
         self._reblock_pending = False
@@ -77,14 +94,17 @@ class GPRF(object):
             if shard is not None:
                 raise ValueError("devices= (one process, several GPUs) and shard= (one process per GPU) exclude each other")
             devices = list(range(devices)) if isinstance(devices, int) else [int(d) for d in devices]
-        self._ctx = _capi.Context(n, dx, Y.shape[1], _capi.DIST_IDS[cov.dfn_str], _capi.KERN_IDS[cov.wfn_str],
-                                  device=device, devices=devices)
+        self._ctx = _capi.Context(n, dx, 0 if kernelized else Y.shape[1], _capi.DIST_IDS[cov.dfn_str],
+                                  _capi.KERN_IDS[cov.wfn_str], device=device, devices=devices)
         self._shard = (int(shard[0]), int(shard[1])) if shard is not None else (0, 1)
         self._group, self._reduce, self._dist_eval = group, bool(reduce), None
         self._multi = devices is not None
         if shard is not None:
             self._ctx.set_shard(*self._shard)
-        self._ctx.set_Y(Y)
+        if kernelized:
+            self._ctx.set_YY(self.YY, self.dy)
+        else:
+            self._ctx.set_Y(Y)
         self._push_theta()
         self._blocks_pushed = None
         self._nbrs_pushed = None
@@ -439,6 +459,18 @@ class GPRF(object):
         if self._multi or self._shard[1] > 1:
             raise NotImplementedError("train_predictor on a sharded / multi-device GPRF: build the predictor from a "
                                       "single-device GPRF")
+        if self.kernelized:
+            # the block alphas need the outputs themselves: a plain model over the same state makes the predictor
+            if Y is None:
+                raise ValueError("train_predictor on a kernelized GPRF needs the outputs: train_predictor(Y=Y)")
+            plain = GPRF(np.array(self.X, dtype=np.float64), np.asarray(Y, dtype=np.float64), self.block_fn, self.cov,
+                         self.noise_var, neighbor_threshold=self.neighbor_threshold,
+                         block_idxs=[np.asarray(b) for b in self.block_idxs], neighbors=list(self.neighbors),
+                         device=self._device)
+            try:
+                return plain.train_predictor(test_cov=test_cov)
+            finally:
+                plain.close()
         from .predict import Predictor
         self.block_idxs                          # (runs a pending re-blocking)
         self._push_blocks()

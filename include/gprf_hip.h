@@ -54,7 +54,8 @@ typedef struct gprf_ctx gprf_ctx;
 #define GPRF_MAX_UNIT 16384
 
 /* Replaces GPRF.__init__ (gprf.py:85-117) + the VectorTree construction (gprf.py:109).
- * n points, dx input dims (2 or 3), dy output columns; device = HIP device ordinal. */
+ * n points, dx input dims (2 or 3), dy output columns (1 ... 64; 0 = kernelized observations, gprf_set_YY);
+ * device = HIP device ordinal. */
 int gprf_create(gprf_ctx **out, int32_t n, int32_t dx, int32_t dy, int32_t dist_id, int32_t kern_id,
                 int32_t device);
 /* The same object over SEVERAL devices of one node, driven from ONE host thread — the reference's drivers are one Python
@@ -84,6 +85,14 @@ const char *gprf_last_error(const gprf_ctx *ctx);
 
 /* self.Y (gprf.py:97): n x dy, uploaded once and kept resident in HBM. */
 int gprf_set_Y(gprf_ctx *ctx, const double *Y);
+
+/* Kernelized observations (GPRF(..., kernelized=True, dy=D), gprf.py:85-97, 674-736): a context created with dy = 0 takes the
+ * outputs as their n x n Gram matrix YY (row-major, exactly symmetric), kept resident in HBM, and dy >= 1 of any size.
+ * gprf_eval / gprf_update_eval / gprf_objective then evaluate every unit as gaussian_llgrad_kernel.  GPRF_ERR_STATE on a plain
+ * context (and gprf_set_Y on a kernelized one); GPRF_ERR_HIP, naming the bytes, when the n x n buffer cannot be allocated.
+ * A kernelized context is single-device: gprf_create_multi, gprf_set_shard, the *_device forms and gprf_predictor_create
+ * refuse it with GPRF_ERR_STATE. */
+int gprf_set_YY(gprf_ctx *ctx, const double *YY, int32_t dy);
 
 /* update_covs (gprf.py:160-167): theta = [noise_var, signal_var, dfn_params...], ntheta = 2 + #dfn_params
  * (euclidean: dx lengthscales; lld: 2). */
